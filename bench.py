@@ -394,6 +394,44 @@ def hip_time(fn, reps):
     return float(np.mean([s.elapsed_time(e) for s, e in ev]))
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: bytes of values in all files together (the .npy headers come on top)
+DUMP_SEED = 2024
+
+
+def dump_positions(n: int, k: int):
+    """positions of the entries --dump-outputs writes of an array of n: all of them when k >= n, else a sorted sample of
+    at most k drawn with DUMP_SEED (the same for every run of the same problem)"""
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=k, dtype=np.int64))
+
+
+def dump_outputs(dirname, mats, vecs):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float64 .npy files -- per matrix the CSR values
+    with the row and column of each (<label>_values, <label>_rows, <label>_cols), per vector its entries with their
+    indices (<label>_values, <label>_index).  Every array gets an equal share of DUMP_BYTES; one that does not fit is
+    represented by a fixed sample of its entries (dump_positions).  Returns the names written."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // max(len(mats) + len(vecs), 1)
+    arrays = {}
+    for label, A in mats.items():
+        vals = A.vals  # (waits for the assembly; block-scalar storage is expanded to the CSR values a caller reads)
+        pos = torch.from_numpy(dump_positions(A.nnz, share // 24)).to(vals.device)
+        arrays[f"{label}_values"] = vals[pos]
+        arrays[f"{label}_rows"] = torch.searchsorted(A.d_rowptr, pos, right=True) - 1
+        arrays[f"{label}_cols"] = A.d_cols[pos]
+    for label, v in vecs.items():
+        vals = v.array  # (completes a posted ghost update)
+        pos = torch.from_numpy(dump_positions(vals.numel(), share // 16)).to(vals.device)
+        arrays[f"{label}_values"] = vals[pos]
+        arrays[f"{label}_index"] = pos
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a.to(torch.float64).cpu().numpy())
+    return list(arrays)
+
+
 def measure_counters(argv_child):
     """Per-kernel PMC counters of one step, measured NOW with rocprofv3 passes of a short child run of this script:
     FETCH_SIZE and WRITE_SIZE (separate passes: TCC has four slots) and one SQ pass (VALU instructions).  Returns
@@ -490,7 +528,7 @@ def main():
                     help="time the CPU baseline on a smaller sample of this resolution instead of the full workload")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-allcores", type=int, default=-1, metavar="P",
-                    help="threads of the all-core CPU leg (default: min(host cores, 64); 0 = skip)")
+                    help="threads of the all-core CPU leg (default: min(OMP_NUM_THREADS or host cores, 64); 0 = skip)")
     ap.add_argument("--cpu-allcores-n", type=int, default=0)
     ap.add_argument("--solve", action="store_true", help="also solve the assembled system (configs 2 / 5): multigrid-CG and Jacobi-CG")
     ap.add_argument("--no-sub-records", action="store_true", help="skip roofline_ufcx / roofline_spatial / roofline_csr_valued")
@@ -508,7 +546,12 @@ def main():
                     help="config 2 with IMPORTED element kernels (UFCx C text -> hipRTC -> LDS row-block kernels): "
                          "'files' = tests/ufcx/laplace_p1_tet.c + source_p1_tet.c, 'generated' = the benchmark's own forms "
                          "as tools/ffcx_like.py writes them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller (matrix values with their rows and "
+                         "columns, vector entries) to DIR/<name>.npy in float64; large arrays as a fixed seeded sample")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.n == 0:
         args.n = int(os.environ.get("MPCX_BENCH_N", {2: 256, 3: 128, 4: 56, 5: 246}[args.config]))
 
@@ -668,6 +711,9 @@ def main():
         dist.all_reduce(cc, op=dist.ReduceOp.SUM)  # doubles as the proof that `world` ranks are in the group
         cells_per_rank = [int(v) for v in cc.cpu().tolist()]
         rccl_ranks = dist.get_world_size()
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, mats, vecs)
+        log(f"outputs of the last timed step: {len(names)} arrays in {args.dump_outputs}")
 
     # ---- per-call and per-kernel timing (HIP events on the launch stream), outside the timed region ----
     reps = max(min(args.steps, 10), 3)
@@ -1202,7 +1248,8 @@ def main():
         except Exception:  # noqa: BLE001
             ram_ok = False
         full = (kind, degree) in (("poisson", 1), ("contact", 0)) and ram_ok and not args.cpu_sample_n
-        P = args.cpu_allcores if args.cpu_allcores >= 0 else min(os.cpu_count() or 1, 64)
+        # (OMP_NUM_THREADS, where set, is the number of cores this process may use; os.cpu_count() counts the whole host)
+        P = args.cpu_allcores if args.cpu_allcores >= 0 else min(int(os.environ.get("OMP_NUM_THREADS") or 0) or os.cpu_count() or 1, 64)
         if full:
             for key, threads in (("cpu_baseline", 1), ("cpu_baseline_allcores", P)):
                 if threads < 1 or (key == "cpu_baseline_allcores" and threads == 1):

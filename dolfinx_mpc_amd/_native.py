@@ -760,5 +760,7 @@ def start_preload():
         except Exception:  # noqa: BLE001  (an optimisation only)
             pass
 
-    _preload_thread = threading.Thread(target=run, name="mpcx-preload", daemon=True)
+    # not a daemon: a process that exits right after the import (``__graft_entry__.build()``) waits for the loads instead of
+    # tearing the HIP runtime down under them (an abort at exit)
+    _preload_thread = threading.Thread(target=run, name="mpcx-preload", daemon=False)
     _preload_thread.start()

@@ -89,3 +89,46 @@ def test_multirank_path_of_every_partitioned_config(nranks, extra):
     assert "error" not in out and out["n_gpus"] == nranks and out["rccl_ranks"] == nranks and out["value"] > 0
     assert "pre-flight over" in r.stderr
     assert out["transport"] is not None
+
+
+def test_dump_positions_are_fixed_and_bounded():
+    """--dump-outputs: a small array is written whole, a large one as the same sorted sample in every run"""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert (bench.dump_positions(10, 10) == list(range(10))).all()
+    p = bench.dump_positions(10 ** 9, 1000)
+    assert 0 < p.size <= 1000 and (p[1:] > p[:-1]).all() and p[0] >= 0 and p[-1] < 10 ** 9
+    assert (bench.dump_positions(10 ** 9, 1000) == p).all()
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's matrix and vector as float64 .npy files within 64 MB; a
+    problem this small is written whole, and two runs with the same arguments dump the same entries"""
+    import numpy as np
+
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--size", "16", "--no-cpu-baseline", "--no-traffic", "--no-config-records", "--no-sub-records",
+                            "--dump-outputs", str(d)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        files = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert set(files) == {"A_values", "A_rows", "A_cols", "b_values", "b_index"}
+        assert all(a.dtype == np.float64 for a in files.values())
+        assert sum(p.stat().st_size for p in d.glob("*.npy")) <= 64 << 20
+        assert files["A_values"].size == out["config"]["nnz_per_gpu"]["A"]
+        assert files["b_values"].size == out["config"]["dofs_per_gpu"]
+        assert np.isfinite(files["A_values"]).all() and np.abs(files["A_values"]).max() > 0
+        assert np.isfinite(files["b_values"]).all() and np.abs(files["b_values"]).max() > 0
+        runs.append(files)
+    for name in ("A_rows", "A_cols", "b_index"):
+        assert (runs[0][name] == runs[1][name]).all()
+    for name in ("A_values", "b_values"):
+        np.testing.assert_allclose(runs[0][name], runs[1][name], rtol=1e-12, atol=1e-14)
